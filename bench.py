@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — benchmarks of the batched OFDM-demodulate + LDPC-decode receive path, one line per BASELINE config.
 
-    python bench.py [--config cfg3] --gpus N --steps K --warmup W
+    python bench.py [--config cfg3] --gpus N --steps K --warmup W [--dump-outputs DIR]
     N > 1 with no launcher around it: bench.py starts its own N ranks (a child `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N ... bench.py --gpus N ...`, before anything touches the GPU).  Under a launcher (RANK / WORLD_SIZE in the
     environment) it is one rank of it and refuses a WORLD_SIZE other than --gpus.  --backend gloo reduces the counters through
@@ -99,12 +99,18 @@ def parse():
     ap.add_argument("--no-build", action="store_true",
                     help="do not (re)build the checker libraries; REQUIRED under rocprofv3, whose preloaded library "
                          "initialises the GPU before main() — the compiler must never be started from such a process")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (float32 or "
+                         "float64, at most 64 MB in all: a fixed seeded sample of rows where the whole output is larger)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def ensure_built(no_build: bool):
     """Build the CHECKER libraries (oracle/libultra_oracle.so, and oracle/_ref when /root/reference exists) BEFORE
-    anything touches the GPU, under a file lock so that the N ranks of a multi-GPU run do not race.  The product
+    anything touches the GPU, under a lock so that the N ranks of a multi-GPU run do not race.  The product
     library is never built here: it must exist (there is no CPU fallback).  After this, oracle.bindings never
     starts the compiler again in this process (ULTRA_ORACLE_NO_BUILD)."""
     lib = ROOT / "projectultra_amd" / "libultra_hip.so"
@@ -117,11 +123,19 @@ def ensure_built(no_build: bool):
             raise SystemExit("oracle/libultra_oracle.so is missing or stale and --no-build was given — run "
                              "`python -c 'import __graft_entry__ as g; g.build()'` (or bench.py once without --no-build) first")
     else:
-        with open(ROOT / "oracle" / ".build.lock", "w") as lock:
+        # the lock is taken on the directory itself, opened read-only: the tree may be one this user cannot write, and with
+        # the libraries up to date (build() made them) make writes nothing either
+        lock = os.open(ROOT / "oracle", os.O_RDONLY)
+        try:
             fcntl.flock(lock, fcntl.LOCK_EX)
             subprocess.check_call(["make", "-s", "-C", str(ROOT / "oracle"), "libultra_oracle.so"], stdout=subprocess.DEVNULL)
-            if Path("/root/reference/src").is_dir():
+            # os.path.isdir is False, not an error, where this user may not enter the directory; nothing is imported from
+            # the tree here, so this file also measures builds of the tree from before oracle.bindings.reference_root
+            ref = "/root/reference/src"
+            if os.path.isdir(ref) and os.access(ref, os.R_OK | os.X_OK):
                 subprocess.check_call(["make", "-s", "-C", str(ROOT / "oracle"), "_ref/libultra_ref.so"], stdout=subprocess.DEVNULL)
+        finally:
+            os.close(lock)
     os.environ["ULTRA_ORACLE_NO_BUILD"] = "1"
 
 
@@ -316,6 +330,10 @@ class ModemWorkload:
     def contexts(self):
         return [self.ctx]
 
+    def outputs(self):
+        """What the last step handed its caller, one row per frame (raw: per stream)."""
+        return self.out
+
     def cpu_baseline(self, cores, sample):
         from oracle.bindings import have_ref, make_config, oracle, Ref
         ccfg = make_config(*self.oracle_cfg)
@@ -502,6 +520,10 @@ class LdpcSweepWorkload:
     def contexts(self):
         return [self.ctx]
 
+    def outputs(self):
+        """The decoder's results, one row per codeword, point-major."""
+        return {k: v.reshape((-1,) + tuple(v.shape[2:])) for k, v in self.out.items()}
+
     def curves(self):
         from projectultra_amd.montecarlo import counters_dict
         return {"LDPC R1_4": [dict(snr_db=s, **counters_dict(c)) for s, c in zip(self.snrs, self.counters.cpu())]}
@@ -588,6 +610,10 @@ class ModeSweepWorkload:
     def contexts(self):
         return self.grid.contexts()
 
+    def outputs(self):
+        """The decoder's results of every code rate, one row per frame of that rate (modulation-major, then point)."""
+        return {f"{k}_{r.name}": v for r, out in zip(self.grid.rates, self.grid.out) for k, v in out.items()}
+
     def curves(self):
         from projectultra_amd.montecarlo import counters_dict
         c = self.counters.cpu()
@@ -638,6 +664,38 @@ class ModeSweepWorkload:
                                     gpu_matches_bitwise=bool(ok_ref))
         self.cores_used = cores
         return res, f"first {per} frames of each of the {len(self.cells) * len(self.snrs)} points (same audio, copied from the device)"
+
+
+DUMP_LIMIT = 64_000_000            # bytes: every file --dump-outputs writes, together
+
+
+def dump_outputs(wl, directory, rank, world, torch):
+    """--dump-outputs: the last step's results (wl.outputs(), one row per trial) and counters as <name>.npy, integers widened
+    exactly (to float32 up to 16 bits, else float64).  Rows that do not fit the budget are sampled: the same seeded, sorted row
+    indices in every array, written as sample_rows.npy.  With N > 1 ranks each writes its own shard as rank<r>_<name>.npy
+    within 1/N of the budget."""
+    def wide(t):
+        if t.dtype == torch.float64 or (not t.dtype.is_floating_point and t.dtype.itemsize > 2):
+            return torch.float64
+        return torch.float32
+
+    rows = wl.outputs()
+    n = {v.shape[0] for v in rows.values()}
+    assert len(n) == 1, {k: tuple(v.shape) for k, v in rows.items()}
+    n = n.pop()
+    counters = wl.counters.to(wide(wl.counters)).cpu().numpy()
+    row_bytes = 8 + sum(wide(v).itemsize * (v.numel() // n) for v in rows.values())      # 8: the row's index
+    k = min(n, (DUMP_LIMIT // world - counters.nbytes - 4096) // row_bytes)                  # 4096: the .npy headers
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(0xD0D0).choice(n, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(wl.counters.device)
+    files = {"sample_rows": idx.astype(np.float64), "counters": counters}
+    files.update({name: v.index_select(0, sel).to(wide(v)).cpu().numpy() for name, v in rows.items()})
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    for name, a in files.items():
+        np.save(out / f"{pre}{name}.npy", a)
+    return {"dir": str(out), "rows": int(n), "rows_written": int(k), "files": sorted(f"{pre}{name}.npy" for name in files)}
 
 
 def self_launch(args) -> int:
@@ -784,6 +842,8 @@ def main():
         wl.step(allreduce)
     barrier()
     elapsed = time.perf_counter() - t0
+    # before the profiled repeat below, which writes the same buffers again
+    dumped = dump_outputs(wl, args.dump_outputs, rank, world, torch) if args.dump_outputs else None
     # The same K steps once more (all ranks: the step holds the collective) with, on rank 0, every kernel launch
     # bracketed by HIP events on the launch stream (ultra_hip_profile_enable) and every all-reduce by a pair of stream
     # events: per-kernel durations for the roofline object.  Kept out of the timed region: the event records cost ~2 %.
@@ -991,6 +1051,8 @@ def main():
         }
         if hasattr(wl, "curves"):
             line["curves"] = wl.curves()
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(line), flush=True)

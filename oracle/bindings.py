@@ -21,6 +21,17 @@ REF_SO = HERE / "_ref" / "libultra_ref.so"
 REFERENCE_ROOT = Path("/root/reference")
 
 
+def reference_root() -> Path | None:
+    """REFERENCE_ROOT when its sources are there and this process may read them, else None.  A user who may not enter the
+    directory above it gets PermissionError from Path.is_dir(), not False: for that user the reference is absent."""
+    try:
+        if (REFERENCE_ROOT / "src").is_dir() and os.access(REFERENCE_ROOT / "src", os.R_OK | os.X_OK):
+            return REFERENCE_ROOT
+    except OSError:
+        pass
+    return None
+
+
 class Config(C.Structure):
     """ultra_hip_config (include/ultra_hip.h) — POD shared with the product ABI."""
     _fields_ = [(n, C.c_uint32) for n in (
@@ -96,7 +107,7 @@ def build_oracle(force=False):
         return
     if force or not ORACLE_SO.exists() or ORACLE_SO.stat().st_mtime < (HERE / "ultra_oracle.c").stat().st_mtime:
         subprocess.check_call(["make", "-C", str(HERE), "libultra_oracle.so"], stdout=subprocess.DEVNULL)
-    if REFERENCE_ROOT.is_dir() and (force or not REF_SO.exists()
+    if reference_root() is not None and (force or not REF_SO.exists()
                                     or REF_SO.stat().st_mtime < (HERE / "ref_shim.cpp").stat().st_mtime):
         subprocess.check_call(["make", "-C", str(HERE), "_ref/libultra_ref.so"], stdout=subprocess.DEVNULL)
 
@@ -607,7 +618,7 @@ def geometry(cfg) -> Geometry:
 def have_ref() -> bool:
     if REF_SO.exists():
         return True
-    if REFERENCE_ROOT.is_dir():
+    if reference_root() is not None:
         try:
             build_oracle()
         except Exception:

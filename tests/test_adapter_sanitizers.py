@@ -11,6 +11,8 @@ projectultra_amd/ or include/ can resolve it (checked below and in tests/test_ab
 
 Each sanitizer is first shown a canary it MUST report (a heap overflow, a data race): a toolchain whose sanitizer is inert
 skips instead of passing vacuously."""
+import platform
+import shutil
 import subprocess
 from pathlib import Path
 
@@ -28,11 +30,25 @@ CANARY = {
             " a.join(); b.join(); return 0; }\n",
 }
 REPORT = ("AddressSanitizer", "ThreadSanitizer", "runtime error:", "LeakSanitizer", "Assertion")
+# what a working sanitizer says about its canary (a ThreadSanitizer that cannot start also prints its name)
+CANARY_REPORT = {"asan": REPORT, "tsan": ("WARNING: ThreadSanitizer: data race",)}
+
+
+def _launcher():
+    """`setarch <machine> -R` where this process may start a program without address-space randomisation, else nothing.  GCC 11's
+    ThreadSanitizer aborts at start-up ("FATAL: ThreadSanitizer: unexpected memory mapping") on kernels whose mmap randomisation
+    (vm.mmap_rnd_bits = 32) puts the executable outside the ranges it knows; newer sanitizer runtimes re-execute themselves the
+    same way.  Only the sanitized programs run like this."""
+    cmd = ["setarch", platform.machine(), "-R"]
+    if shutil.which("setarch") and subprocess.run(cmd + ["true"], capture_output=True).returncode == 0:
+        return cmd
+    return []
 
 
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
     out = tmp_path_factory.mktemp("adapter_san")
+    launch = _launcher()
     built = {}
     for kind, flags in FLAGS.items():
         canary = out / f"canary_{kind}.cpp"
@@ -42,14 +58,14 @@ def drivers(tmp_path_factory):
         if r.returncode != 0:
             built[kind] = (None, f"g++ {flags[0]} does not link here: {r.stderr[-300:]}")
             continue
-        c = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-        if not any(w in c.stderr for w in REPORT):
-            built[kind] = (None, f"{flags[0]} is inert in this container (the canary's defect was not reported)")
+        c = subprocess.run([*launch, str(exe)], capture_output=True, text=True, timeout=120)
+        if not any(w in c.stderr for w in CANARY_REPORT[kind]):
+            built[kind] = (None, f"{flags[0]} is inert in this container (the canary's defect was not reported): {c.stderr[-300:]}")
             continue
         drv = out / f"adapter_driver_{kind}"
         subprocess.check_call(["g++", "-std=c++20", *flags, f"-I{ROOT / 'include'}", str(STUB / "ultra_hip_teststub.cpp"),
                                str(STUB / "adapter_driver.cpp"), "-o", str(drv), "-lpthread"])
-        built[kind] = (drv, None)
+        built[kind] = ([*launch, str(drv)], None)
     return built
 
 
@@ -57,7 +73,7 @@ def _run(drivers, kind, scenario, seed):
     drv, why = drivers[kind]
     if drv is None:
         pytest.skip(why)
-    r = subprocess.run([str(drv), scenario, str(seed)], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([*drv, scenario, str(seed)], capture_output=True, text=True, timeout=600)
     reports = [l for l in r.stderr.splitlines() if any(w in l for w in REPORT) or l.startswith("FAIL")]
     assert not reports and r.returncode == 0, (scenario, seed, r.returncode, reports[:6], r.stderr[-1500:])
     assert f"{scenario} seed {seed}: 0 failures" in r.stdout

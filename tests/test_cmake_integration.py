@@ -18,14 +18,15 @@ from pathlib import Path
 import pytest
 
 from _refprogs import TOOLS, require, run
+from oracle.bindings import reference_root
 
 ROOT = Path(__file__).resolve().parent.parent
-REF = Path("/root/reference")
+REF = reference_root()
 BUILT = ROOT / "integration" / "_build" / "BUILT"
 BIN = ROOT / "integration" / "_build" / "bin"
 
 
-@pytest.mark.skipif(not REF.is_dir() or shutil.which("cmake") is None, reason="needs cmake and /root/reference (the build container)")
+@pytest.mark.skipif(REF is None or shutil.which("cmake") is None, reason="needs cmake and /root/reference (the build container)")
 def test_reference_cmake_configures_and_builds_over_the_drop_ins(tmp_path, hiplib):
     b = tmp_path / "b"
     subprocess.check_call(["cmake", "-S", str(ROOT / "integration"), "-B", str(b), f"-DULTRA_REFERENCE={REF}"], stdout=subprocess.DEVNULL)

@@ -6,8 +6,10 @@ profiles/README.md and BASELINE.md: present in this repository — or, for the r
 import re
 from pathlib import Path
 
+from oracle.bindings import reference_root
+
 ROOT = Path(__file__).resolve().parent.parent
-REF = Path("/root/reference")
+REF = reference_root()
 DOCS = ["README.md", "DESIGN.md", "INTEGRATION.md", "profiles/README.md", "BASELINE.md"]
 PATH = re.compile(r"`((?:profiles|tests|tools|oracle|projectultra_amd|include)/[A-Za-z0-9_./\-]+)`")
 
@@ -21,9 +23,9 @@ def test_cited_paths_exist():
                 continue
             if (ROOT / path).exists():
                 continue
-            if path.startswith("oracle/_ref/"):                       # built artefacts: git-ignored, present only where the reference was compiled
+            if (path + "/").startswith("oracle/_ref/"):               # built artefacts: git-ignored, present only where the reference was compiled
                 continue
-            if re.match(r"(tests|tools)/[A-Za-z0-9_]+(\.cpp)?$", path) and (not REF.is_dir() or (REF / path).exists() or (REF / (path + ".cpp")).exists()):
+            if re.match(r"(tests|tools)/[A-Za-z0-9_]+(\.cpp)?$", path) and (REF is None or (REF / path).exists() or (REF / (path + ".cpp")).exists()):
                 continue                                              # a program of the reference, cited by its path there
             missing.append((doc, path))
     assert not missing, missing
