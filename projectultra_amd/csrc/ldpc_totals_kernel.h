@@ -117,6 +117,35 @@ __device__ __forceinline__ void tprof_store_totals(const float (&t)[VR]) {
                         "v"(t[VR > 6 ? 6 : 0]) : "m0", "memory");
 }
 
+// SIGN BITS (round 7; the regular codes' instances with WANT_TOTAL = false: kSignBits below).  The reference's sign rule is
+// `x < 0` (:185-200, :227-230), which is not the sign bit for -0.0 (sign bit set, not < 0) and for NaN (never < 0).  The channel values are canonicalised once,
+// where they are staged: -0.0 -> +0.0, NaN (either sign, any payload) -> +inf.  Every output stays bit-identical (bytes, iters,
+// ok), and from then on no value of the loop is -0.0 or NaN, so `x < 0` IS the sign bit:
+//   1. every c2v is bit-identical: it reads `v < 0` and |v| only; +-0 agree on both, and so do NaN and +inf — neither is < 0 and
+//      neither is ever a minimum (the cap, FLT_MAX or 50, is below inf; minNum drops a NaN).  By induction over the iterations.
+//   2. a total T = llr_in + sum of c2v (each finite) differs from the reference's at most as +0 against -0 or +inf against NaN:
+//      rounding to nearest gives -0.0 only when every addend is -0.0, and llr_in no longer is; +inf + finite = +inf.
+//   3. a message v = T - c2v is -0.0 only if T is, and NaN only if T is: neither happens.
+//   4. hard decisions (T < 0) and the parity verdict therefore agree bit for bit; the unchecked information bits are read from
+//      memory in the output step, not from the staged copy.
+// The WANT_TOTAL instance writes T itself, where the sign of a zero and a NaN show: it keeps `x < 0` and the raw values.
+// Cost: two compares and two selects per staged value, once per codeword; tools/ldpc_signbit_check.cpp replays it on the host.
+// Only the regular codes (R2/3, R3/4, R5/6: six information edges in every row round) use it: the low-rate instances, already
+// spilling at their register budgets, spill more with it and ran 2-19 % slower (profiles/r07_variants/r07_ab_signbits_low_rates.txt).
+constexpr bool ldpc_rows_regular(unsigned long long prof, int rounds) {
+    for (int r = 0; r < rounds; ++r) if (ldpc_prof(prof, r) != 6) return false;
+    return true;
+}
+constexpr unsigned kLdpcSignBit = 0x80000000u, kLdpcThreeQuartersBits = 0x3f400000u;   // the bits of 0.75f
+template <bool ON>
+__device__ __forceinline__ float ldpc_sign_canon(float x) {
+    if constexpr (!ON) return x;
+    // integer tests: independent of the denormal mode
+    const unsigned u = __float_as_uint(x);
+    if ((u & ~kLdpcSignBit) > 0x7f800000u) return __uint_as_float(0x7f800000u);   // NaN -> +inf
+    return __uint_as_float(u == kLdpcSignBit ? 0u : u);                          // -0.0 -> +0.0
+}
+
 // RR row rounds, VR variable rounds; RPROF / VPROF: S_r / D_r, four bits per round (LdpcTPlan::row_prof / var_prof).  WAVES:
 // wavefronts per SIMD the register budget is sized for.  WANT_TOTAL: also write the final a-posteriori LLRs (parity tests).
 // The totals kernel names its LDS planes by immediate offsets behind M0 = 0 (ds_write_addtid_b32), i.e. it assumes that a
@@ -147,6 +176,7 @@ __global__ __launch_bounds__(kLdpcThreads, WAVES) void ldpc_totals_kernel(
     if (work_list != nullptr && work_counter[kScreenCtlSample] >= gate) { lst = work_list; n_work = (int)work_counter[kScreenCtlDirty]; }
     if ((int)blockIdx.x >= n_work) return;         // any one wavefront drains every queue: the others are not needed
     constexpr bool kPacked = RR >= 8;          // R1/4's instance: packed single-precision subtract / multiply / add (row phase below)
+    constexpr bool kSignBits = !WANT_TOTAL && ldpc_rows_regular(RPROF, RR);   // sign bits as the signs (ldpc_sign_canon)
     // block_len > 0 (ultra_hip_ldpc_decode_blocks): codeword c is row (c / block_len) * block_stride + c % block_len of the
     // LLR array — several equally long runs of rows inside a larger array (one code rate's share of a mode grid) decoded
     // by ONE launch; results stay dense (row c).
@@ -309,12 +339,12 @@ __global__ __launch_bounds__(kLdpcThreads, WAVES) void ldpc_totals_kernel(
         float llr_v[VR], llr_p[RR], c2v[RR][7];
 #pragma unroll
         for (int r = 0; r < VR; ++r) {
-            llr_v[r] = ldsf(kRowStage ? (unsigned)src_v[r] : STAGE_V + (unsigned)(r * 64 + lane) * 4u);   // an empty slot reads a stale word: never used
+            llr_v[r] = ldpc_sign_canon<kSignBits>(ldsf(kRowStage ? (unsigned)src_v[r] : STAGE_V + (unsigned)(r * 64 + lane) * 4u));   // an empty slot reads a stale word: never used
             store_linear((unsigned)(r * 256), llr_v[r]);                       // total before any iteration = llr_in
         }
 #pragma unroll
         for (int r = 0; r < RR; ++r) {
-            llr_p[r] = ldsf(kRowStage ? (unsigned)src_p[r] : STAGE_P + (unsigned)(r * 64 + lane) * 4u);
+            llr_p[r] = ldpc_sign_canon<kSignBits>(ldsf(kRowStage ? (unsigned)src_p[r] : STAGE_P + (unsigned)(r * 64 + lane) * 4u));
 #pragma unroll
             for (int t = 0; t < 7; ++t) c2v[r][t] = 0.0f;                      // check_to_var starts at 0 (:175)
         }
@@ -340,16 +370,24 @@ __global__ __launch_bounds__(kLdpcThreads, WAVES) void ldpc_totals_kernel(
                 constexpr int r = decltype(round)::value;
                 constexpr int S = ldpc_prof(RPROF, r);                         // information-edge slots of this round; the parity edge is edge S
                 float v[7], mn[7], tot[6];
-                bool ng[7], par = false;
                 // total of the parity bit after the previous iteration: llr_in + c2v (:206-213; the bit has one edge)
                 const float tp = llr_p[r] + c2v[r][S];
                 if (WANT_TOTAL) tpar[r] = tp;
 #pragma unroll
                 for (int t = 0; t < S; ++t) tot[t] = ldsf(taddr[r][t]);       // a row with fewer edges reads a pad word: FLT_MAX
                 if (all_hold) {                                                // uniform branch
-                    bool synd = tp < 0;
+                    bool synd;
+                    if constexpr (kSignBits) {
+                        // sign bits (ldpc_sign_canon): the xor of the S + 1 words is negative iff an odd number of them are < 0
+                        unsigned x = __float_as_uint(tp);
 #pragma unroll
-                    for (int t = 0; t < S; ++t) synd ^= (tot[t] < 0);          // hard decisions of :227-230
+                        for (int t = 0; t < S; ++t) x ^= __float_as_uint(tot[t]);
+                        synd = (int)x < 0;
+                    } else {
+                        synd = tp < 0;
+#pragma unroll
+                        for (int t = 0; t < S; ++t) synd ^= (tot[t] < 0);      // hard decisions of :227-230
+                    }
                     all_hold = (__ballot(synd) & row_mask[r]) == 0ull;
                 }
                 // var_to_check = llr_total - check_to_var (:216-219).  kPacked (R1/4's instance): two edges per instruction — a
@@ -373,10 +411,25 @@ __global__ __launch_bounds__(kLdpcThreads, WAVES) void ldpc_totals_kernel(
                         for (int t = 0; t <= S; ++t) v[t] = full[t] - c2v[r][t];
                     }
                 }
+                if constexpr (kSignBits) {
+                    // sign * min * 0.75f (:201) as min * (+-0.75f): the factor's sign bit is the xor of the OTHER edges' sign bits
+                    // (ldpc_sign_canon: here a sign bit is exactly `v < 0`).  +-1 * min is exact and rounding to nearest is
+                    // symmetric, so min * -0.75f == -(min * 0.75f) bit for bit; min >= +0, so a zero message gets the sign
+                    // the reference's product gives it.  No compare, no select, no lane mask on the scalar unit: the row's xor
+                    // is S two-cycle v_xor_b32, each factor one v_bitop3_b32 (profiles/r07_issue_table_bitop3.txt).
+                    unsigned x = 0u;
 #pragma unroll
-                for (int t = 0; t <= S; ++t) { ng[t] = v[t] < 0; par ^= ng[t]; }
-                leave_one_out_min<S + 1>(v, cap, mn);
-                {
+                    for (int t = 0; t <= S; ++t) x ^= __float_as_uint(v[t]);
+                    const unsigned q = (x & kLdpcSignBit) | kLdpcThreeQuartersBits;   // +-0.75f, the sign of the whole row
+                    leave_one_out_min<S + 1>(v, cap, mn);
+#pragma unroll
+                    for (int t = 0; t <= S; ++t)                                       // min * (q ^ (v & sign))
+                        c2v[r][t] = mn[t] * __uint_as_float(__builtin_amdgcn_bitop3_b32(q, __float_as_uint(v[t]), kLdpcSignBit, 0x78));
+                } else {
+                    bool ng[7], par = false;
+#pragma unroll
+                    for (int t = 0; t <= S; ++t) { ng[t] = v[t] < 0; par ^= ng[t]; }
+                    leave_one_out_min<S + 1>(v, cap, mn);
                     float mag[7];
                     if constexpr (kPacked) {
 #pragma unroll
